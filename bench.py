@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Device-resident Parquet page-decode benchmark (BASELINE.json metric) on MI355X.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config all|levels|dict|delta|alltypes] [...]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                  [--config all|levels|dict|delta|alltypes] [...]
 
 A step is one decode of the whole synthetic workload through the C ABI with the page bytes
 already resident in HBM:
@@ -11,14 +12,27 @@ already resident in HBM:
   configs[3] (`delta`): DELTA_BINARY_PACKED INT64, 1e9 values, 128-value mini-blocks;
   configs[4] (`alltypes`): this GPU's share of the alltypes_plain-schema file (88 row groups of
       2^23 rows, ~64 GiB decoded): row groups partitioned over the ranks.
-The default (`all`) times every config in one run; the JSON line's top level is configs[1], the
-others are under "configs". With --gpus N > 1 and no WORLD_SIZE in the environment, this process
+A plain run does only what the headline figure needs: it generates and uploads the workload of
+configs[1] (or of the one config --config names), warms up, times --steps decodes, writes the
+outputs of the last timed step when --dump-outputs is given, and prints the JSON line (metric,
+value, unit, higher_is_better, dtype, ms_per_step and the step's algorithmic bytes). Everything
+else is behind --full: with it the default (`all`) times every config in one run (the JSON line's
+top level is configs[1], the others are under "configs"), each with its value check against the
+generator, stage and dominant-kernel times, rooflines, variants, the PCIe-inclusive rate, the CPU
+baseline and the copy ceiling. With --gpus N > 1 and no WORLD_SIZE in the environment, this process
 starts N ranks through torch.distributed.run (before touching the GPU) and exits with their
 status; every rank decodes its own partition: weak scaling, no collective on the data path (gloo
 carries the barrier and the max-over-ranks step time). Rank 0 prints one JSON line.
 
-ms_per_step is timed on the production kernel sequence with stage timing off; a second, shorter
-pass with HIP events on the decode stream (pqg_ctx_set_timing) gives the dominant kernel's time
+--dump-outputs DIR writes what the last timed step of the top-level config left in its output
+buffers (the arrays a caller of the decode receives) as DIR/<name>.npy: a fixed, seeded sample of
+each array (sample_index: both ends and random positions between), float32 for levels and raw
+bytes, float64 for int32 values and offsets, int64 values as two exact float64 halves (<name>_hi,
+<name>_lo). The workload is generated from --seed, so two runs with the same arguments decode
+identical pages and sample identical positions.
+
+ms_per_step is timed on the production kernel sequence with stage timing off; with --full a second,
+shorter pass with HIP events on the decode stream (pqg_ctx_set_timing) gives the dominant kernel's time
 for the roofline. The CPU baseline is the C restatement of parquet-rs's decode loop (oracle/,
 kind "port") on a bounded sample, one decoder per thread, at 1 thread and at the host threads
 this process may use, batch sizes 32/64/128/1024 (benches/decoding.rs:103-123,
@@ -50,6 +64,11 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: every config of `all`, value checks, stage times, "
+                         "rooflines, variants, PCIe-inclusive rate, CPU baseline, copy ceiling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's outputs (top-level config) as DIR/<name>.npy")
     ap.add_argument("--config", default="all", choices=["all", "levels", "dict", "delta", "alltypes"])
     ap.add_argument("--n", type=float, default=1e9, help="levels/values per GPU")
     ap.add_argument("--p-null", type=float, default=0.0, help="configs[1]: null fraction of the def levels")
@@ -59,14 +78,14 @@ def parse(argv=None):
     ap.add_argument("--block-size", type=int, default=512)
     ap.add_argument("--mini-blocks", type=int, default=4)
     ap.add_argument("--variants", type=int, default=1,
-                    help="also time the p_null 0.5 / 0.1 variants (config 2) and the writer-default DELTA "
+                    help="--full: also time the p_null 0.5 / 0.1 variants (config 2) and the writer-default DELTA "
                          "block shape, 128 values in 4 mini-blocks of 32 (config 4, encoding.rs:508-509)")
     ap.add_argument("--split", default="auto", choices=["auto", "weak", "strong"],
                     help="configs 2-4 over N ranks: weak = every rank decodes its own 1e9-value stream; "
                          "strong = the ranks split one 1e9-value stream into contiguous page ranges "
                          "(SURVEY 8(e)); auto = weak, plus a strong-scaling line per config when N > 1")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
-    ap.add_argument("--pcie", type=int, default=1, help="also time the host-to-host (PCIe) rate")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: the CPU baseline legs")
+    ap.add_argument("--pcie", type=int, default=1, help="--full: also time the host-to-host (PCIe) rate")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline budget of the headline")
     ap.add_argument("--threads", type=int, default=16, help="host threads at most (box CPU share: 16)")
     ap.add_argument("--seed", type=int, default=0x5EED0000)
@@ -264,6 +283,66 @@ def check_values(ctx, w, stream):
     return {"pages_checked": checked, "status": st, "values": int(w.out.num_values)}
 
 
+def sample_index(n, seed, k=1 << 20, edge=1 << 16):
+    """Positions of [0, n) that --dump-outputs keeps: the first and the last `edge` and k seeded
+    random ones between, ascending; every position when n is no larger than that."""
+    if n <= k + 2 * edge:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(seed)
+    return np.concatenate([np.arange(edge, dtype=np.int64), np.sort(rng.integers(edge, n - edge, k)),
+                           np.arange(n - edge, n, dtype=np.int64)])
+
+
+def _gather(t, seed, **kw):
+    """The sample_index elements of device tensor t, on the host."""
+    import torch
+    idx = torch.from_numpy(sample_index(t.numel(), seed, **kw)).to(t.device)
+    return t.index_select(0, idx).cpu().numpy()
+
+
+def _save(out_dir, rank, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, (name if rank == 0 else f"rank{rank}_{name}") + ".npy"), a)
+
+
+def dump_fixed(w, out_dir, rank, seed):
+    """configs[1..3]: what the last decode left in the caller's buffers (def levels, values)."""
+    import torch
+    arrays = {}
+    if w.d_def is not None:
+        arrays["def_levels"] = _gather(w.d_def[:w.out.num_levels], seed).astype(np.float32)
+    nv = int(w.out.num_values)
+    if w.es == 4:
+        arrays["values"] = _gather(w.d_val[:4 * nv].view(torch.int32), seed + 1).astype(np.float64)
+    else:  # int64 does not fit a float64: two 32-bit halves, each exact
+        v = _gather(w.d_val[:8 * nv].view(torch.int64), seed + 1)
+        arrays["values_hi"] = (v >> 32).astype(np.float64)
+        arrays["values_lo"] = (v & 0xFFFFFFFF).astype(np.float64)
+    _save(out_dir, rank, arrays)
+
+
+def dump_alltypes(w, last, out_dir, rank, seed):
+    """Config 5: every column (def levels, the values' bytes, BYTE_ARRAY offsets) of the row groups
+    whose outputs the last pass left in place. last: (row group, output set, its Output structs)
+    per such row group (alltypes_steps.last)."""
+    import pqgtools
+    arrays = {}
+    kw = {"k": 1 << 17, "edge": 1 << 14}
+    for g, oset, outs in last:
+        for j, (name, pt) in enumerate(pqgtools.ALLTYPES):
+            d_def, d_val, d_off, _ = w.out[oset][j]
+            o = outs[j]
+            nb = w.info[g].value_bytes[j]
+            key = f"rg{w.rg_index[g]}_{name}"
+            arrays[key + "_def_levels"] = _gather(d_def[:o.num_levels], seed, **kw).astype(np.float32)
+            arrays[key + "_value_bytes"] = _gather(d_val[:nb], seed + 1, **kw).astype(np.float32)
+            if d_off is not None:
+                arrays[key + "_offsets"] = _gather(d_off[:o.num_values + 1], seed + 2, **kw).astype(np.float64)
+    _save(out_dir, rank, arrays)
+
+
 def time_steps(ctx, w, stream, steps, warmup, dist=None):
     """Seconds per step over `steps` decodes, production path (no stage events)."""
     import torch
@@ -449,19 +528,35 @@ LEVEL_NOTE = ("HIP events around pqg_launch_levels: the def-level kernel chain (
 
 
 def run_fixed(pqgpu, ctx, args, world, rank, dist, stream, kind, p_null=None, steps=None, warmup=None,
-              cpu_seconds=None, extras=True, block=None, variant=None, strong=False):
-    """One of configs[1..3]: generate, check, time (production path), stage times, roofline, and
-    on rank 0 of a 1-GPU run the PCIe-inclusive rate and the CPU baseline. strong: the ranks split
-    one stream into contiguous page ranges (value = the stream's units / the slowest rank's time)."""
+              cpu_seconds=None, extras=True, block=None, variant=None, strong=False, dump=None):
+    """One of configs[1..3]: generate, time (production path), write the outputs (dump: a
+    directory); with --full also check before timing, stage times, roofline, and on rank 0 of a
+    1-GPU run the PCIe-inclusive rate and the CPU baseline. strong: the ranks split one stream into
+    contiguous page ranges (value = the stream's units / the slowest rank's time)."""
     import torch
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     w = Workload(pqgpu, args, rank, kind, p_null=p_null, block=block, world=world, strong=strong)
-    checked = check_values(ctx, w, stream)
+    checked = check_values(ctx, w, stream) if args.full else None
     per_step = max_over_ranks(time_steps(ctx, w, stream, steps, warmup, dist), dist)
-    tm = time_stages(pqgpu, ctx, w, stream, max(3, steps // 4), args.overlap)
+    if dump:
+        dump_fixed(w, dump, rank, args.seed)
     units = w.levels if kind == "levels" else w.values
     step_bytes = w.in_bytes + w.out_bytes
+    # the stream each rank decodes: its own (weak) or its page range of the shared one (strong)
+    job_units = (w.n if strong else units * world)
+    if not args.full:  # the headline alone: the step time and the step's algorithmic bytes
+        res = {"value": job_units / per_step, "unit": "levels/s" if kind == "levels" else "values/s",
+               "ms_per_step": per_step * 1e3,
+               "gbps": None if strong else step_bytes / per_step / 1e9 * world,  # strong: needs a reduction
+               "config": {"levels_per_gpu": w.levels, "values_per_gpu": w.values, "pages_per_gpu": w.npages,
+                          "page_values": args.page_values, "p_null": w.p_null,
+                          "in_bytes_per_gpu": w.in_bytes, "out_bytes_per_gpu": w.out_bytes,
+                          "gen_seconds": round(w.gen_s, 1)}}
+        del w
+        torch.cuda.empty_cache()
+        return res
+    tm = time_stages(pqgpu, ctx, w, stream, max(3, steps // 4), args.overlap)
     if kind == "levels":
         lev_b = w.level_bytes_in + 2 * w.levels   # level stream in + int16 levels out
         val_b = 2 * w.values * w.es               # PLAIN values in + out
@@ -489,8 +584,6 @@ def run_fixed(pqgpu, ctx, args, world, rank, dist, stream, kind, p_null=None, st
     dom = max(rl, key=lambda r: r["avg_ms"] or 0)
     if kind == "levels" and p_null:
         dom = rl[0]
-    # the stream each rank decodes: its own (weak) or its page range of the shared one (strong)
-    job_units = (w.n if strong else units * world)
     res = {
         "value": job_units / per_step,
         "unit": "levels/s" if kind == "levels" else "values/s",
@@ -767,19 +860,23 @@ def alltypes_check(ctx, w, stream, batch_ctx=None):
             "path": "pqg_decode_chunks (whole step)" if batch_ctx is not None else "pqg_rg_decode"}
 
 
-def alltypes_steps(ctx, w, stream, steps, warmup, dist=None, batch_ctx=None):
+def alltypes_steps(ctx, w, stream, steps, warmup, dist=None, batch_ctx=None, enqueue=True):
     """Every row group of the share per step: one batched decode of all their column chunks
     (batch_ctx), or one row-group decode per row group alternating between two launch streams and
-    two output sets, so that row group g + 1's kernels start while g's still run."""
+    two output sets, so that row group g + 1's kernels start while g's still run. enqueue: also
+    time the host enqueue of a pass alone (three more passes). alltypes_steps.last names the row
+    groups whose outputs the last timed pass left in place (for dump_alltypes)."""
     import torch
     lanes = [stream, torch.cuda.Stream().cuda_stream]
+    nc = len(w.cols)
 
     def one_pass():
         if batch_ctx is not None:
-            w.decode_step(batch_ctx, stream)
-            return
+            oa = w.decode_step(batch_ctx, stream)
+            return [(g, g, oa[g * nc:(g + 1) * nc]) for g in sorted({0, w.R - 1})]
         for g in range(w.R):
-            w.decode_rg(ctx, g, lanes[g % 2], g % 2)
+            oa = w.decode_rg(ctx, g, lanes[g % 2], g % 2)
+        return [(w.R - 1, (w.R - 1) % 2, oa)]
 
     sync = (lambda: batch_ctx.sync_detail()) if batch_ctx is not None else (lambda: ctx.sync())
     for _ in range(warmup):
@@ -790,7 +887,7 @@ def alltypes_steps(ctx, w, stream, steps, warmup, dist=None, batch_ctx=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_pass()
+        alltypes_steps.last = one_pass()
     th = time.perf_counter()
     r = sync()
     torch.cuda.synchronize()
@@ -799,6 +896,9 @@ def alltypes_steps(ctx, w, stream, steps, warmup, dist=None, batch_ctx=None):
         dist.barrier()
     assert r[0] == 0, r
     alltypes_steps.host_ms = (th - t0) / steps * 1e3  # enqueue time per step (host side)
+    alltypes_steps.enqueue_ms = None
+    if not enqueue:
+        return (t1 - t0) / steps
     # the enqueue alone: with the GPU idle, no wait for a staging slot is inside it
     enq = []
     for _ in range(3):
@@ -910,17 +1010,22 @@ def alltypes_cpu_baseline(w, threads, thr_info):
             "by_threads": {f"{th}t_b1024": round(v[0], 1) for th, v in res.items()}}
 
 
-def run_alltypes(pqgpu, args, world, rank, dist, stream, extras=True):
+def run_alltypes(pqgpu, args, world, rank, dist, stream, extras=True, dump=None):
     import torch
     w = AlltypesWorkload(pqgpu, args, rank, world)
     ctx = pqgpu.RowGroupDecoder(torch.cuda.current_device(), args.streams)
     bctx = pqgpu.Context(torch.cuda.current_device()) if args.at_batch == "step" else None
     if bctx is not None:
         bctx.set_overlap(args.overlap)
-    checked = alltypes_check(ctx, w, stream, bctx)
-    if bctx is not None:
-        checked["row_group_path"] = alltypes_check(ctx, w, stream)  # the row-group decoder too
-    per_step = max_over_ranks(alltypes_steps(ctx, w, stream, args.steps, args.warmup, dist, bctx), dist)
+    checked = None
+    if args.full:
+        checked = alltypes_check(ctx, w, stream, bctx)
+        if bctx is not None:
+            checked["row_group_path"] = alltypes_check(ctx, w, stream)  # the row-group decoder too
+    per_step = max_over_ranks(alltypes_steps(ctx, w, stream, args.steps, args.warmup, dist, bctx,
+                                             enqueue=args.full), dist)
+    if dump:
+        dump_alltypes(w, alltypes_steps.last, dump, rank, args.seed)
     step_bytes = w.in_bytes + w.out_bytes
     achieved = step_bytes / per_step / 1e9
     # traffic: the PMC bytes of every decode kernel of one step (one pqg_decode_chunks per step)
@@ -948,7 +1053,7 @@ def run_alltypes(pqgpu, args, world, rank, dist, stream, extras=True):
         "host_enqueue_ms_per_step": getattr(alltypes_steps, "enqueue_ms", None),
         "host_ms_per_step_in_loop": getattr(alltypes_steps, "host_ms", None),
     }
-    if extras and rank == 0 and world == 1:
+    if extras and args.full and rank == 0 and world == 1:
         if args.pcie:
             res["pcie_inclusive"] = alltypes_file_pipeline(pqgpu, w, args)
         if args.cpu_baseline:
@@ -997,9 +1102,11 @@ def main(argv=None):
     stream = torch.cuda.current_stream().cuda_stream
     head = {"metric": METRIC, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "higher_is_better": True, "scaling": "strong" if args.split == "strong" else "weak", "vs_baseline": None,
-            "data": "synthetic pages from reference-identical writers (SplitMix64 seeded)"}
+            "data": "synthetic pages from reference-identical writers (SplitMix64 seeded)", "full": args.full}
     sub = {}
-    kinds = ["levels", "dict", "delta", "alltypes"] if args.config == "all" else [args.config]
+    # `all`: every config with --full, the headline (configs[1]) alone without
+    kinds = [args.config] if args.config != "all" else ["levels", "dict", "delta", "alltypes"] if args.full else ["levels"]
+    variants = args.variants and args.full
     ctx = pqgpu.Context(torch.cuda.current_device())
     ctx.set_overlap(args.overlap)
     short_steps = max(5, args.steps // 2)
@@ -1016,13 +1123,14 @@ def main(argv=None):
 
     for kind in kinds:
         if kind == "alltypes":
-            sub[kind] = run_alltypes(pqgpu, args, world, rank, dist, stream)
+            sub[kind] = run_alltypes(pqgpu, args, world, rank, dist, stream,
+                                     dump=args.dump_outputs if kind == kinds[0] else None)
             continue
         unit_key = "levels_per_s" if kind == "levels" else "values_per_s"
         if kind == "levels":
             sub[kind] = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, "levels", p_null=args.p_null,
-                                  strong=strong)
-            if args.variants:
+                                  strong=strong, dump=args.dump_outputs if kind == kinds[0] else None)
+            if variants:
                 var = {}
                 for p in (0.5, 0.1):
                     r = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, "levels", p_null=p,
@@ -1030,8 +1138,9 @@ def main(argv=None):
                     var[f"p_null={p}"] = brief(r, unit_key)
                 sub[kind]["variants"] = var
         else:
-            sub[kind] = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, kind, cpu_seconds=6.0, strong=strong)
-            if kind == "delta" and args.variants:
+            sub[kind] = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, kind, cpu_seconds=6.0, strong=strong,
+                                  dump=args.dump_outputs if kind == kinds[0] else None)
+            if kind == "delta" and variants:
                 # the reference writer's default block (DeltaBitPackEncoder: 128 values, 4 mini-blocks
                 # of 32, encoding.rs:508-509): the shape real parquet-rs files carry
                 r = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, "delta", steps=short_steps, warmup=2,
@@ -1040,7 +1149,7 @@ def main(argv=None):
                 # DELTA_BYTE_ARRAY / DELTA_LENGTH_BYTE_ARRAY: one 2^20-value page each
                 for enc in ("dba", "dlba"):
                     sub[kind]["variants"][f"{enc}_page_1M"] = run_bytes_page(pqgpu, ctx, stream, enc, short_steps, 2)
-        if args.split == "auto" and world > 1:
+        if args.split == "auto" and world > 1 and args.full:
             # strong scaling alongside: the ranks split one 1e9-value stream into page ranges
             r = run_fixed(pqgpu, ctx, args, world, rank, dist, stream, kind,
                           p_null=args.p_null if kind == "levels" else None, steps=short_steps, warmup=2,
@@ -1055,10 +1164,11 @@ def main(argv=None):
     if len(kinds) > 1:
         result["configs"] = {k: sub[k] for k in kinds[1:]}
     if rank == 0:
-        try:
-            result["copy_ceiling_gbs"] = copy_ceiling_gbs()
-        except Exception as e:  # pragma: no cover
-            result["copy_ceiling_gbs"] = str(e)
+        if args.full:
+            try:
+                result["copy_ceiling_gbs"] = copy_ceiling_gbs()
+            except Exception as e:  # pragma: no cover
+                result["copy_ceiling_gbs"] = str(e)
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -4,5 +4,5 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out/r06_bench
-timeout -k 10 600 python bench.py > gpurun_out/r06_bench/bench.json 2> gpurun_out/r06_bench/bench.err || exit 1
+(cd "$_" && timeout -k 10 600 python "$R/bench.py" --full > bench.json 2> bench.err) || exit 1  # in the directory made above
 bash tools/profile.sh alltypes r06_at --variants 0 --pcie 0 --cpu-baseline 0 || exit 1

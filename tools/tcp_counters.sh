@@ -15,7 +15,7 @@ P2="TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE"
 for i in 1 2; do
   eval P=\$P$i
   timeout -k 10 120 rocprofv3 --pmc $P -d "$O/dict_p$i" -o run --output-format csv -- \
-    python3 "$R/bench.py" --config dict --steps 1 --warmup 0 --cpu-baseline 0 --variants 0 --pcie 0 > "$O/dict_p$i.log" 2>&1 || exit 1
+    python3 "$R/bench.py" --full --config dict --steps 1 --warmup 0 --cpu-baseline 0 --variants 0 --pcie 0 > "$O/dict_p$i.log" 2>&1 || exit 1
   timeout -k 10 120 rocprofv3 --pmc $P -d "$O/gather_p$i" -o run --output-format csv -- \
     "$R/tools/ubench/gather_ubench" > "$O/gather_p$i.log" 2>&1 || exit 1
 done
