@@ -258,8 +258,14 @@ __device__ inline void lv_fallback_page(const uint8_t* __restrict__ blob, uint64
   Stream s;
   if (!get_stream(blob, pw, sel, ck.cp, s)) return;
   if (threadIdx.x < 64) {
-    const int32_t st = run_index(blob, blob_len, s, rt.ck + pw.ltile0, rt.runs + (uint64_t)pw.ltile0 * RUN_CAPT,
-                                 rt.nruns + pw.ltile0, ism);
+    int32_t st = run_index(blob, blob_len, s, rt.ck + pw.ltile0, rt.runs + (uint64_t)pw.ltile0 * RUN_CAPT,
+                           rt.nruns + pw.ltile0, ism);
+    // A level stream that ends before the page's levels (no next header, a cut varint, a
+    // truncated bit-packed run: run_index's ST_EOF) is no error to the reference's level decoder:
+    // it returns a short batch (levels.rs:249-271, rle.rs:398-434), read_batch serves it, then
+    // reads nothing more and never advances (column/reader.rs:182-262): ST_HANG. With rep levels
+    // the def / rep counts may disagree first; those columns keep the decoder's status.
+    if (st == ST_EOF && ck.cp.max_rep == 0) st = ST_HANG;
     if (threadIdx.x == 0) {
       st_s = st;
       if (st) report(pages, chunks, p, st);
@@ -296,10 +302,11 @@ __global__ void __launch_bounds__(WG) k_lv_fallback(const uint8_t* __restrict__ 
                                                     uint32_t* ctr, int scan, int npages) {
   // a grid of at most LF_GRID workgroups strides over the pages (handed-back pages are rare: a
   // workgroup per page made the launch itself cost ~10 us more)
-  for (int p = (int)blockIdx.x; p < npages; p += (int)gridDim.x) {
-    lv_fallback_page(blob, blob_len, pages, chunks, tile_page, sel, rt, p);
-    __syncthreads();  // (the page's shared state before the next page's)
-  }
+  if (*rt.nfall != 0)  // (no handed-back page: only the scan is left)
+    for (int p = (int)blockIdx.x; p < npages; p += (int)gridDim.x) {
+      lv_fallback_page(blob, blob_len, pages, chunks, tile_page, sel, rt, p);
+      __syncthreads();  // (the page's shared state before the next page's)
+    }
   if (scan && last_workgroup(ctr)) scan_values(pages, chunks, npages);
 }
 

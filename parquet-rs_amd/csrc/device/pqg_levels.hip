@@ -5,7 +5,12 @@
 // Run headers sit at data-dependent offsets: where a header starts depends on every header
 // before it. Two ways to find them, chosen per page by the page itself:
 //
-//   k_lv_plan    windows (1 KiB of stream) per page (exclusive scan), eligibility of each stream.
+//   k_lv_plan    windows (1 KiB of stream) per page (exclusive scan), eligibility of each stream;
+//                a stream that is one RLE run holding all its outputs (lv_run_only: no nulls in the
+//                page, an all-null page) is a walked page at once, its run list written here, and
+//                needs none of the kernels below up to its emit. The plan also counts the pages of
+//                every path (LvCount); each kernel below loads its path's count first and returns
+//                when it is 0.
 //   k_lv_walk    one wave per page walks the header chain: a scalar hop loop follows up to 64
 //                headers in an LDS-staged 4 KiB region (one LDS read and a few scalar ops per
 //                one-byte header), then the 64 lanes parse those headers together, check them,
@@ -281,8 +286,13 @@ __device__ inline void lv_first_hops(const uint32_t* stage, uint32_t sb, uint32_
 }
 
 // Exclusive scan of per-page window counts over one workgroup (pages in order).
-template <class F>
-__device__ inline void lv_scan_windows(int npages, uint32_t* wbase, F nwin_of) {
+struct LvNoPlace {
+  __device__ inline void operator()(int, uint32_t, uint32_t) const {}
+};
+
+// place(p, first window, windows): called for every page by the thread that scanned it.
+template <class F, class P = LvNoPlace>
+__device__ inline void lv_scan_windows(int npages, uint32_t* wbase, F nwin_of, P place = P{}) {
   __shared__ uint32_t wsum[WG / 64];
   __shared__ uint32_t carry_s;
   if (threadIdx.x == 0) carry_s = 0;
@@ -300,7 +310,10 @@ __device__ inline void lv_scan_windows(int npages, uint32_t* wbase, F nwin_of) {
     __syncthreads();
     uint32_t pre = carry_s;
     for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) pre += wsum[k];
-    if (p < npages) wbase[p] = pre + incl - nw;
+    if (p < npages) {
+      wbase[p] = pre + incl - nw;
+      place(p, pre + incl - nw, nw);
+    }
     __syncthreads();
     if (threadIdx.x == WG - 1) carry_s = pre + incl;
     __syncthreads();
@@ -350,8 +363,29 @@ __device__ inline bool lv_d1_page(const LevelTables& lt, int p, const Stream& s,
          (uint64_t)s.n * 16u <= (uint64_t)s.slen * PQG_D1_LPB16;
 }
 
+// A stream that is one RLE run holding every output the reader asks for ("no nulls in this page",
+// an all-null page, a flat list's rep levels): the header at offset 0, parsed by the walkers' fast
+// parse (lv_parse_xy: a varint of <= 4 bytes, header and value inside the stream), is an RLE run
+// of at least n outputs whose value fits the bit width. The reader stops at n outputs
+// (rle.rs:490-508), so the bytes after the run do not matter. Anything else — count 0, a shorter
+// run, a wider value, a cut header — stays with the paths that reproduce the reference's errors.
+// run: (run length, run-record info word).
+__device__ inline bool lv_run_only(const uint8_t* __restrict__ blob, const Stream& s, uint2& run) {
+  if (s.n == 0 || s.slen == 0) return false;
+  const uint32_t w = (uint32_t)s.w, vb = (w + 7u) >> 3;
+  uint32_t b[2] = {0u, 0u};  // the stream's first 6 bytes (zeros past its end: the length check refuses them)
+  const uint32_t m = min(s.slen, 6u);
+  for (uint32_t i = 0; i < m; ++i) b[i >> 2] |= (uint32_t)blob[s.S + i] << (8u * (i & 3u));
+  uint32_t nxt, cnt, val;
+  bool bp;
+  if (!lv_parse_xy(b[0], b[1], 0u, s.slen, w, vb, nxt, cnt, val, bp)) return false;
+  if (bp || cnt < s.n || (val >> w) != 0u) return false;
+  run = make_uint2(cnt, R_RLE | val);
+  return true;
+}
+
 __global__ void __launch_bounds__(WG) k_lv_plan(const uint8_t* __restrict__ blob, PageWork* pages, int npages,
-                                                const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
+                                                ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
   // one thread per page: flag, window and segment counts (into wbase / sbase, scanned in place
   // by the last workgroup; a single workgroup paid the pages' dependent loads four at a time)
   const int p = (int)(blockIdx.x * WG + threadIdx.x);
@@ -366,7 +400,18 @@ __global__ void __launch_bounds__(WG) k_lv_plan(const uint8_t* __restrict__ blob
         flag = PF_PAGE;
         nw = s.n ? (s.slen + LV_WIN - 1) / LV_WIN : 0u;
         if (sel == SS_DEF) pages[p].nonnull = 0;
-        if (lv_d1_page(lt, p, s, sel)) {  // dense one-bit levels: the chunk walks (pqg_lvd1.hpp)
+        uint2 run;
+        if (lv_run_only(blob, s, run)) {
+          // a walked page without a front end: no segments, neither a D1 nor a window-path
+          // candidate whatever the density probe said; the last workgroup writes its run list
+          flag = PF_WALK;
+          lt.runp[p] = run;
+          // (one atomic per wave and chunk where a wave's pages belong to one chunk: a thousand
+          // atomics on one word cost the plan ~15 us)
+          const uint64_t act = __ballot(true);
+          if (pw.chunk != rfl(pw.chunk) || (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(act))
+            atomicOr(&chunks[pw.chunk].res.paths, PATH_LEVEL_RUNS);
+        } else if (lv_d1_page(lt, p, s, sel)) {  // dense one-bit levels: the chunk walks (pqg_lvd1.hpp)
           flag = PF_D1;
           ns = (s.slen + LW_SEGW * LV_WIN - 1) / (LW_SEGW * LV_WIN);
         } else if (!lt.dense[p] && s.n && s.slen) {
@@ -383,8 +428,48 @@ __global__ void __launch_bounds__(WG) k_lv_plan(const uint8_t* __restrict__ blob
     lt.sbase[p] = ns;
   }
   if (last_workgroup(lt.ctr + 2)) {
-    lv_scan_windows(npages, lt.wbase, [&](int q) -> uint32_t { return lt.wbase[q]; });
+    // beside the window scan: the page counts the later kernels test first (LvCount), and the run
+    // lists of the run-only pages, in the form k_lv_compact writes: the run, the sentinel (the
+    // run's end), and the first run of every window — window 0 holds the one header, the others
+    // and the end none. (The page's flag, probe result and run are loaded with its window count:
+    // one round trip per 256 pages; the run is stale unless the page is run-only.)
+    __shared__ uint32_t cnt_s[4];
+    if (threadIdx.x < 4) cnt_s[threadIdx.x] = 0;  // (the scan's first barrier orders this)
+    uint32_t nd1 = 0, nsparse = 0, npage = 0, nwalk = 0, f = 0, dense = 0;
+    uint2 run = make_uint2(0u, 0u);
+    lv_scan_windows(
+        npages, lt.wbase,
+        [&](int q) -> uint32_t {
+          f = rt.pflag[q];
+          dense = lt.dense[q];
+          run = lt.runp[q];
+          return lt.wbase[q];
+        },
+        [&](int q, uint32_t k0, uint32_t nwin) {
+          nd1 += f == PF_D1;
+          npage += f == PF_PAGE;
+          nsparse += f == PF_PAGE && !dense;
+          if (f != PF_WALK) return;
+          ++nwalk;
+          uint2* rec = lt.rec + (uint64_t)LW_REC * (k0 + 2ull * (uint32_t)q);
+          uint32_t* wf = lt.wfirst + k0 + (uint32_t)q;
+          rec[0] = make_uint2(0u, run.y);
+          rec[1] = make_uint2(run.x, 0u);
+          wf[0] = 0u;
+          for (uint32_t kw = 1; kw <= nwin; ++kw) wf[kw] = 1u;
+        });
     lv_scan_windows(npages, lt.sbase, [&](int q) -> uint32_t { return lt.sbase[q]; });
+    if (nd1) atomicAdd(&cnt_s[0], nd1);
+    if (nsparse) atomicAdd(&cnt_s[1], nsparse);
+    if (npage) atomicAdd(&cnt_s[2], npage);
+    if (nwalk) atomicAdd(&cnt_s[3], nwalk);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      lt.ctr[LC_D1] = cnt_s[0];
+      lt.ctr[LC_SPARSE] = cnt_s[1];
+      lt.ctr[LC_PAGE] = cnt_s[2];
+      lt.ctr[LC_WALK] = cnt_s[3] + cnt_s[1];
+    }
   }
 }
 
@@ -487,6 +572,7 @@ __global__ void __launch_bounds__(WG) k_lv_bound(const uint8_t* __restrict__ blo
                                                  const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
   __shared__ uint32_t stg[WG / WAVE][LB_STG / 4];
   __shared__ uint32_t hist_s[WG / WAVE][LB_BINS];
+  if (lt.ctr[LC_SPARSE] == 0) return;  // no page for the segment walk (LvCount)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   uint32_t* st = stg[wid];
   uint32_t* hist = hist_s[wid];
@@ -612,6 +698,7 @@ __global__ void __launch_bounds__(WG) k_lv_segwalk(const uint8_t* __restrict__ b
                                                    const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
   __shared__ uint32_t stg[WG / WAVE][LW_STG / 4];
   __shared__ uint4 lent_s[WG / WAVE][LW_STG / 8];  // per staged byte (u16): 2 * hop length of a one-byte header
+  if (lt.ctr[LC_SPARSE] == 0) return;  // no page for the segment walk (LvCount)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   // LDS address of this wave's hop-length table
   const uint32_t lb = rfl((uint32_t)(uintptr_t)(__attribute__((address_space(3))) const uint4*)lent_s[wid]);
@@ -1027,10 +1114,17 @@ __device__ inline void lv_segscan_page(const uint8_t* __restrict__ blob, const P
 __global__ void __launch_bounds__(WG) k_lv_segscan(const uint8_t* __restrict__ blob, const PageWork* __restrict__ pages,
                                                    int npages, const ChunkWork* chunks, int sel, RunTables rt,
                                                    LevelTables lt) {
-  for (uint32_t p = blockIdx.x; p < (uint32_t)npages; p += gridDim.x) {
-    lv_segscan_page(blob, pages, npages, chunks, sel, rt, lt, p);
-    __syncthreads();  // (the page's shared state before the next page's)
+  // (LvCount; both words are the same for every workgroup of the grid, so the ticket below is
+  // taken by all of them or by none)
+  if (lt.ctr[LC_PAGE] == 0) {  // no page can reach the window path: its kernels test this total
+    if (blockIdx.x == 0 && threadIdx.x == 0) lt.wbase2[npages] = 0;
+    return;
   }
+  if (lt.ctr[LC_SPARSE] != 0)
+    for (uint32_t p = blockIdx.x; p < (uint32_t)npages; p += gridDim.x) {
+      lv_segscan_page(blob, pages, npages, chunks, sel, rt, lt, p);
+      __syncthreads();  // (the page's shared state before the next page's)
+    }
   if (last_workgroup(lt.ctr + 0)) lv_plan2_scan(npages, rt, lt);
 }
 
@@ -1039,6 +1133,7 @@ __global__ void __launch_bounds__(WG) k_lv_segscan(const uint8_t* __restrict__ b
 // made page-relative), the first run of every window whose start lies before one of its headers,
 // and after the page's last run a sentinel and the windows past it.
 __global__ void __launch_bounds__(WG) k_lv_compact(int npages, RunTables rt, LevelTables lt) {
+  if (lt.ctr[LC_SPARSE] == 0) return;  // no page went through the segment walk (LvCount)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   const uint32_t total = lt.sbase[npages];
   for (uint32_t sidx = blockIdx.x * (WG / WAVE) + wid; sidx < total; sidx += gridDim.x * (WG / WAVE)) {
@@ -1305,6 +1400,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) k_
                                                const PageWork* __restrict__ pages, int npages,
                                                const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
   __shared__ LvSmem sm;
+  if (lt.wbase2[npages] == 0) return;  // no window left to the window path (k_lv_segscan)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   LvWave& W = sm.wv[wid];
   LvDense D;
@@ -1558,6 +1654,7 @@ __global__ void __launch_bounds__(SC_WG) k_lv_stitch(const uint8_t* __restrict__
   __shared__ uint64_t wacc[SC_NW];
   __shared__ uint64_t acc_s;
   __shared__ uint32_t e_s, ok_s, serial_s, nv_s;
+  if (lt.wbase2[npages] == 0) return;  // no window left to the window path (k_lv_segscan)
   const uint32_t p = blockIdx.x, tid = threadIdx.x, wid = tid >> 6, lane = tid & 63u;
   if (p >= (uint32_t)npages || rt.pflag[p] != PF_PAGE) return;
   const PageWork& pw = pages[p];
@@ -2514,6 +2611,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) k_
                                                 PageWork* pages, int npages, const ChunkWork* chunks, int sel,
                                                 RunTables rt, LevelTables lt) {
   __shared__ LvSmem sm;
+  if (lt.wbase2[npages] == 0) return;  // no window left to the window path (k_lv_segscan)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   LvWave& W = sm.wv[wid];
   LvDense D;
@@ -2869,6 +2967,7 @@ __global__ void __launch_bounds__(WG) k_lv_emit_walk(const uint8_t* __restrict__
   using WaveT = LeWaveT<Writer::PIPE ? LE_STG : LE_STG_U>;
   __shared__ WaveT sm[WG / WAVE];
   __shared__ uint32_t smx[WG / WAVE][Writer::XW];
+  if (lt.ctr[LC_WALK] == 0) return;  // no walked page (LvCount)
   const uint32_t wid = rfl(threadIdx.x >> 6), lane = threadIdx.x & 63u;
   WaveT& E = sm[wid];
   uint32_t* xw = smx[wid];
@@ -3052,7 +3151,7 @@ __global__ void __launch_bounds__(WG) k_lv_emit_walk(const uint8_t* __restrict__
 
 // Plan, segment starts and walks, page scan, run compaction: every page of stream `sel` ends
 // walked (PF_WALK, its run list built), dense (PF_PAGE) or handed back (PF_BAIL).
-static void lv_front(const uint8_t* blob, uint64_t blob_len, PageWork* pages, int npages, const ChunkWork* chunks,
+static void lv_front(const uint8_t* blob, uint64_t blob_len, PageWork* pages, int npages, ChunkWork* chunks,
                      int sel, RunTables rt, LevelTables lt, uint32_t wgrid, hipStream_t s) {
   if (sel == SS_BOOL)  // (def / rep: k_prepare probed them; dictionary indices: cleared there)
     hipLaunchKernelGGL(k_lv_probe, dim3((npages + WG / WAVE - 1) / (WG / WAVE)), dim3(WG), 0, s, blob, blob_len,

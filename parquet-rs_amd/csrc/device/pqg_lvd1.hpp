@@ -307,6 +307,7 @@ __global__ void __launch_bounds__(WG) k_d1_tab(const uint8_t* __restrict__ blob,
                                                const PageWork* __restrict__ pages, int npages,
                                                const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt) {
   __shared__ D1TabSmem sm;
+  if (lt.ctr[LC_D1] == 0) return;  // no page for the chunk walks (LvCount)
   const uint32_t c = threadIdx.x;
   D1Range G;
   if (!G.begin(lt, npages)) return;
@@ -419,9 +420,10 @@ __global__ void __launch_bounds__(WG) k_d1_stitch(const uint8_t* __restrict__ bl
   __shared__ uint2 tb[64 * D1_ENT];
   __shared__ uint32_t e_s, jn_s, state_s;
   __shared__ uint64_t acc_s;
+  if (lt.ctr[LC_D1] == 0) return;  // no page for the chunk walks (LvCount)
   for (int p = (int)blockIdx.x; p < npages; p += (int)gridDim.x) {
     Stream s;
-    if (rt.pflag[p] != PF_D1 || !lv_stream(blob, pages[p], sel, chunks, s)) continue;
+    if (rt.pflag[p] != PF_D1|| !lv_stream(blob, pages[p], sel, chunks, s)) continue;
     const uint32_t g0 = lt.sbase[p], ns = lt.sbase[p + 1] - g0, n = s.n, slen = s.slen;
     __syncthreads();  // (the previous page's shared state)
     if (threadIdx.x == 0) {
@@ -493,6 +495,7 @@ __global__ void __launch_bounds__(WG) k_d1_emit(const uint8_t* __restrict__ blob
                                                 PageWork* pages, int npages, const ChunkWork* chunks, int sel,
                                                 RunTables rt, LevelTables lt) {
   __shared__ D1EmitSmem sm;
+  if (lt.ctr[LC_D1] == 0) return;  // no page for the chunk walks (LvCount)
   const uint32_t c = threadIdx.x;
   D1Range G;
   if (!G.begin(lt, npages)) return;

@@ -132,7 +132,7 @@ struct Slot {
   DeltaTables dt = {};   // DELTA_BINARY_PACKED tiled path
   size_t dt_tcap = 0, dt_pcap = 0;
   // level path (pqg_levels.hip): buffers of LevelTables per stream kind, grown on demand
-  static constexpr int LV_BUFS = 14;  // wbase, wbase2, wfirst, rec, tab, win, sbase, bexit, seg, srec, spos, dense, ctr, bmp
+  static constexpr int LV_BUFS = 15;  // wbase, wbase2, wfirst, rec, tab, win, sbase, bexit, seg, srec, spos, dense, ctr, bmp, runp
   void* lvbuf[K_N][LV_BUFS] = {};
   size_t lvcap[K_N][LV_BUFS] = {};
   uint32_t* bail = nullptr;  // PQG_DIAG, PQG_DEBUG 512: LevelTables::bail of the def stream
@@ -152,6 +152,7 @@ struct Slot {
     t.dense = (uint32_t*)lvbuf[k][11];
     t.ctr = (uint32_t*)lvbuf[k][12];
     t.bmp = (uint16_t*)lvbuf[k][13];
+    t.runp = (uint2*)lvbuf[k][14];
     t.tstride = tstride;
     t.bail = k == K_DEF ? bail : nullptr;
     return t;
@@ -878,9 +879,9 @@ static int decode_batch(pqg_ctx* ctx, uint32_t nc, const pqg_column* cols, const
     const size_t need[Slot::LV_BUFS] = {(size_t)np + 1, (size_t)np + 1, nwin + np + 1,
                                         64 * (nwin + 2 * (size_t)np) + 1, (nwin + 1) * ent, nwin + 1,
                                         (size_t)np + 1, nseg, nseg, nseg * LW_SCAP, nseg * LW_SCAP,
-                                        (size_t)np + 1, 16, (nwin + 1) * 64};
+                                        (size_t)np + 1, 16, (nwin + 1) * 64, (size_t)np + 1};
     const size_t elem[Slot::LV_BUFS] = {4, 4, 4, sizeof(uint2), sizeof(uint2), sizeof(uint2),
-                                        4, 4, sizeof(LvSeg), sizeof(uint2), 4, 4, 4, 2};
+                                        4, 4, sizeof(LvSeg), sizeof(uint2), 4, 4, 4, 2, sizeof(uint2)};
     const bool fresh_ctr = sl.lvbuf[k][12] == nullptr;
     for (int bb = 0; bb < Slot::LV_BUFS; ++bb)
       if ((st = grow(ctx, &sl.lvbuf[k][bb], &sl.lvcap[k][bb], need[bb], elem[bb], "hipMalloc level tables"))) return st;
@@ -1124,6 +1125,8 @@ int pqg_sync_detail(pqg_ctx* ctx, int* bad_call, int* bad_chunk, int* bad_page) 
     int ch, pg;
     std::string m;
     const int c = sl->call;
+    if (sl == &ctx->slot[ctx->cur])  // the last decode: the path bits its kernels set
+      for (size_t j = 0; j < sl->ch.size(); ++j) ctx->paths |= sl->h_res[j].res.paths;
     const int s2 = finish_slot(*sl, &ch, &pg, m);
     if (s2 && !st) {
       st = s2;
@@ -1163,6 +1166,8 @@ int pqg_get_timings(pqg_ctx* ctx, pqg_timings* t) {
   t->values_kernel = ctx->values_kernel;
   return PQG_OK;
 }
+
+static_assert(PATH_LEVEL_RUNS == PQG_PATH_LEVEL_RUNS, "device path bit mirrors the header");
 
 int pqg_ctx_last_paths(pqg_ctx* ctx, uint32_t* mask) {
   if (!ctx || !mask) return PQG_ERR_INVALID;

@@ -94,7 +94,10 @@ struct ChunkResult {
   uint64_t total_bytes;
   uint64_t bad;            // lowest failing page (chunk-relative) and its status: (page << 32) | status;
                            // ~0 when clean
+  uint32_t paths;          // PQG_PATH_* bits only the device knows (PQG_PATH_LEVEL_RUNS: k_lv_plan)
+  uint32_t pad;
 };
+constexpr uint32_t PATH_LEVEL_RUNS = 256u;  // mirrors PQG_PATH_LEVEL_RUNS (include/pqgpu.h)
 
 // Outputs per expand tile of the RLE/bit-packed hybrid decoder (device/pqg_runs.hpp).
 constexpr uint32_t RUN_TILE = 4096;
@@ -209,10 +212,26 @@ struct LevelTables {
   uint32_t* dense;   // [pages] 1: the stream's first 64 headers lie within 1 KiB (k_lv_probe): the
                      // window path takes it without a segment walk
   uint32_t* ctr;     // [16] last-workgroup tickets (zero between launches): [0] k_lv_segscan,
-                     // [1] k_lv_fallback, [2] k_lv_plan
+                     // [1] k_lv_fallback, [2] k_lv_plan; then the page counts of LvCount, written by
+                     // k_lv_plan's last workgroup on every decode
+  uint2* runp;       // [pages] run-only pages (k_lv_plan): (run length, run-record info word)
   uint32_t tstride;  // tab entries per window: lv_ent of the widest stream of the decode (the
                      // streams of a batch's chunks may differ in bit width)
   uint32_t* bail;    // PQG_DIAG builds, PQG_DEBUG 512: per page, where the level path handed it back
+};
+
+// LevelTables::ctr words past the tickets: how many pages k_lv_plan gave each path. The kernels of
+// a path load their word first and return when it is 0, so a path without pages costs a launch
+// and one scalar load. The counts are upper bounds for everything after the plan: a later kernel
+// moves a page only out of its path to PF_BAIL (lv_bail: the segment scan, both stitches, the
+// emits), never into one, with one exception, k_lv_segscan, which turns a sparse candidate into a
+// walked page (PF_WALK: counted in LC_WALK beforehand) or leaves it PF_PAGE for the window path
+// (counted in LC_PAGE; the window kernels test wbase2's total, scanned after that decision).
+enum LvCount : uint32_t {
+  LC_D1 = 3,      // PF_D1 pages
+  LC_SPARSE = 4,  // PF_PAGE pages the segment walk takes (not dense)
+  LC_PAGE = 5,    // PF_PAGE pages, dense or not: those the window path can get
+  LC_WALK = 6,    // pages k_lv_emit_walk can get: run-only pages and the sparse candidates
 };
 
 // RunTables::pflag values: stream decoded by the level path (pqg_levels.hip) — by its window
