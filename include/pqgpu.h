@@ -187,8 +187,8 @@ int pqg_get_timings(pqg_ctx *ctx, pqg_timings *t);
 int pqg_reset_timings(pqg_ctx *ctx);
 const char *pqg_error_message(pqg_ctx *ctx);
 /* The value-kernel families the last decode enqueued (diagnostics and tests: which path a page
- * shape takes), a mask of PQG_PATH_*. PQG_PATH_LEVEL_RUNS is decided on the device: it is valid
- * once that decode has been synchronised (pqg_sync), and 0 before. */
+ * shape takes), a mask of PQG_PATH_*. The PQG_PATH_LEVEL_* bits are decided on the device: they
+ * are valid once that decode has been synchronised (pqg_sync), and 0 before. */
 enum {
   PQG_PATH_PLAIN = 1,          /* fixed-width PLAIN copy */
   PQG_PATH_DICT_LEVEL = 2,     /* dictionary indices on the level path (LDS dictionary) */
@@ -198,7 +198,10 @@ enum {
   PQG_PATH_DELTA_BYTES = 32,   /* DELTA_BYTE_ARRAY slice rebuild */
   PQG_PATH_DELTA = 64,         /* DELTA_BINARY_PACKED */
   PQG_PATH_RLE_BOOL = 128,     /* RLE booleans */
-  PQG_PATH_LEVEL_RUNS = 256    /* a hybrid stream that is one RLE run: settled by the level path's plan */
+  PQG_PATH_LEVEL_RUNS = 256,   /* a hybrid stream that is one RLE run: settled by the level path's plan */
+  PQG_PATH_LEVEL_D1 = 512,     /* a dense one-bit def / rep stream the plan gave to the chunk walks */
+  PQG_PATH_LEVEL_HANDBACK = 1024 /* a stream the plan gave to the level path, handed back by a later
+                                    kernel to the general decoder (not: left to it by the plan) */
 };
 int pqg_ctx_last_paths(pqg_ctx *ctx, uint32_t *mask);
 

@@ -241,21 +241,26 @@ __device__ inline bool lv_stream(const uint8_t* blob, const PageWork& pw, int se
          lv_width_ok((uint32_t)s.w) && (sel != SS_DICT || (ck.lvdict && (uint32_t)s.w <= ck.cp.dict_maxw));
 }
 
-// Hand page p to the general decoder (once).
-__device__ inline void lv_bail(RunTables& rt, uint32_t p, uint32_t from) {
-  if (atomicCAS(&rt.pflag[p], from, PF_BAIL) == from) atomicAdd(rt.nfall, 1u);
+// Hand page p to the general decoder (once); its chunk reports PATH_LEVEL_HANDBACK (the path word
+// of the chunk's result is the one word of `chunks` the kernels that can hand a page back write).
+__device__ inline void lv_bail(RunTables& rt, const PageWork* pages, ChunkWork* chunks, uint32_t p,
+                               uint32_t from) {
+  if (atomicCAS(&rt.pflag[p], from, PF_BAIL) == from) {
+    atomicAdd(rt.nfall, 1u);
+    atomicOr(&chunks[pages[p].chunk].res.paths, PATH_LEVEL_HANDBACK);
+  }
 }
 // The same, recording in diagnostic builds where (lt.bail, PQG_DEBUG 512): 1 segment scan,
 // 2 stitch, 4 emit: a chain walk or run check, 5 emit: a run of the bitmap writes, 6 / 7
 // walked-page emit.
 #ifdef PQG_DIAG
-#define LV_BAIL(rt, lt, p, from, site)                               \
+#define LV_BAIL(rt, lt, pages, chunks, p, from, site)                \
   do {                                                               \
     if ((lt).bail) atomicCAS(&(lt).bail[p], 0u, (uint32_t)(site));  \
-    lv_bail(rt, p, from);                                            \
+    lv_bail(rt, pages, chunks, p, from);                             \
   } while (0)
 #else
-#define LV_BAIL(rt, lt, p, from, site) lv_bail(rt, p, from)
+#define LV_BAIL(rt, lt, pages, chunks, p, from, site) lv_bail(rt, pages, chunks, p, from)
 #endif
 
 // Own positions' first hop (window-relative next offset, terminal codes >= LV_WIN) and output
@@ -413,6 +418,9 @@ __global__ void __launch_bounds__(WG) k_lv_plan(const uint8_t* __restrict__ blob
             atomicOr(&chunks[pw.chunk].res.paths, PATH_LEVEL_RUNS);
         } else if (lv_d1_page(lt, p, s, sel)) {  // dense one-bit levels: the chunk walks (pqg_lvd1.hpp)
           flag = PF_D1;
+          const uint64_t act = __ballot(true);  // (one atomic per wave and chunk, as above)
+          if (pw.chunk != rfl(pw.chunk) || (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(act))
+            atomicOr(&chunks[pw.chunk].res.paths, PATH_LEVEL_D1);
           ns = (s.slen + LW_SEGW * LV_WIN - 1) / (LW_SEGW * LV_WIN);
         } else if (!lt.dense[p] && s.n && s.slen) {
           const uint32_t sw = lw_segw((uint32_t)s.w);
@@ -979,7 +987,7 @@ __device__ inline uint32_t lv_segscan_serial(LvSeg* seg, const uint2* srec, uint
 }
 
 __device__ inline void lv_segscan_page(const uint8_t* __restrict__ blob, const PageWork* __restrict__ pages,
-                                       int npages, const ChunkWork* chunks, int sel, RunTables rt, LevelTables lt,
+                                       int npages, ChunkWork* chunks, int sel, RunTables rt, LevelTables lt,
                                        uint32_t p) {
   __shared__ uint64_t wout[WG / WAVE];
   __shared__ uint32_t wrun[WG / WAVE], wlast[WG / WAVE], wmin[WG / WAVE];
@@ -1102,7 +1110,7 @@ __device__ inline void lv_segscan_page(const uint8_t* __restrict__ blob, const P
     if (verdict == 1 && sel == SS_DICT) verdict = 2;  // no window path for dictionary indices
     verdict_s = verdict;
     if (verdict == 0) rt.pflag[p] = PF_WALK;
-    else if (verdict == 2) LV_BAIL(rt, lt, p, PF_PAGE, 1);
+    else if (verdict == 2) LV_BAIL(rt, lt, pages, chunks, p, PF_PAGE, 1);
   }
   __syncthreads();
   if (verdict_s != 0)
@@ -1112,7 +1120,7 @@ __device__ inline void lv_segscan_page(const uint8_t* __restrict__ blob, const P
 // The grid's last workgroup also runs k_lv_plan2's scan (the windows of the pages left to the
 // window path), one launch fewer per level stream.
 __global__ void __launch_bounds__(WG) k_lv_segscan(const uint8_t* __restrict__ blob, const PageWork* __restrict__ pages,
-                                                   int npages, const ChunkWork* chunks, int sel, RunTables rt,
+                                                   int npages, ChunkWork* chunks, int sel, RunTables rt,
                                                    LevelTables lt) {
   // (LvCount; both words are the same for every workgroup of the grid, so the ticket below is
   // taken by all of them or by none)
@@ -1646,7 +1654,7 @@ __device__ inline uint32_t sc_rl(const uint32_t (&v)[EPL], uint32_t e) {
 template <uint32_t EPL>  // entries per lane (ent / 64): 1, 2 (readlane walks: streams of bit width 1 / 2) or
                         // 0 (any ent, LDS walks: wider streams)
 __global__ void __launch_bounds__(SC_WG) k_lv_stitch(const uint8_t* __restrict__ blob, const PageWork* __restrict__ pages,
-                                                     int npages, const ChunkWork* chunks, int sel, RunTables rt,
+                                                     int npages, ChunkWork* chunks, int sel, RunTables rt,
                                                      LevelTables lt) {
   __shared__ uint2 tb[SC_ENT];
   __shared__ uint2 F[SC_FENT];  // per composing wave and entry offset: (exit entry | SC_SPEC, outputs)
@@ -1826,7 +1834,7 @@ __global__ void __launch_bounds__(SC_WG) k_lv_stitch(const uint8_t* __restrict__
   if (tid == 0) {
     bool ok = ok_s != 0;
     if (serial_s) ok = lv_stitch_serial(tab, win, nw, ent, ts, n, slen);
-    if (!ok) LV_BAIL(rt, lt, p, PF_PAGE, 2);
+    if (!ok) LV_BAIL(rt, lt, pages, chunks, p, PF_PAGE, 2);
   }
 }
 
@@ -2608,7 +2616,7 @@ __device__ inline bool lv_ref_headers(const uint32_t* stage, uint32_t* pm, const
 // Window path: windows g2 of the dense pages.
 template <int OUT>
 __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) k_lv_emit(const uint8_t* __restrict__ blob, uint64_t blob_len,
-                                                PageWork* pages, int npages, const ChunkWork* chunks, int sel,
+                                                PageWork* pages, int npages, ChunkWork* chunks, int sel,
                                                 RunTables rt, LevelTables lt) {
   __shared__ LvSmem sm;
   if (lt.wbase2[npages] == 0) return;  // no window left to the window path (k_lv_segscan)
@@ -2801,7 +2809,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) k_
       }
     }
     if (__ballot(bad)) {
-      if (lane == 0) LV_BAIL(rt, lt, x.p, PF_PAGE, 4);
+      if (lane == 0) LV_BAIL(rt, lt, pages, chunks, x.p, PF_PAGE, 4);
 #ifdef PQG_DIAG
       // (the first failing window of the page: its index + 1, stitch entry, first output)
       if (lt.bail && lane == 0 && atomicCAS(&lt.bail[npages + 4 * x.p], 0u, x.k + 1u) == 0u) {
@@ -2821,7 +2829,7 @@ __global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4))) k_
                                        (uint64_t)base + myacc, n);
         LE_STAMP(2)
         if (cnt == 0xFFFFFFFFu) {
-          if (lane == 0) LV_BAIL(rt, lt, x.p, PF_PAGE, 5);
+          if (lane == 0) LV_BAIL(rt, lt, pages, chunks, x.p, PF_PAGE, 5);
         } else {
           lv_bm_store<OUT>(reinterpret_cast<const uint32_t*>(W.JC), x, B, cnt, sel, pages, gp(D.out));
         }
@@ -2962,7 +2970,7 @@ __device__ inline void le_install(const LeLoad& f, WaveT& E) {
 
 template <class Writer>
 __global__ void __launch_bounds__(WG) k_lv_emit_walk(const uint8_t* __restrict__ blob, uint64_t blob_len,
-                                                     PageWork* pages, int npages, const ChunkWork* chunks,
+                                                     PageWork* pages, int npages, ChunkWork* chunks,
                                                      int sel, RunTables rt, LevelTables lt, Writer wr) {
   using WaveT = LeWaveT<Writer::PIPE ? LE_STG : LE_STG_U>;
   __shared__ WaveT sm[WG / WAVE];
@@ -3055,7 +3063,7 @@ __global__ void __launch_bounds__(WG) k_lv_emit_walk(const uint8_t* __restrict__
       if (fr == fe) continue;
       const uint32_t R = fe - fr;
       if (R > LW_RPW) {
-        if (lane == 0) LV_BAIL(rt, lt, p, PF_WALK, 6);
+        if (lane == 0) LV_BAIL(rt, lt, pages, chunks, p, PF_WALK, 6);
         continue;
       }
       const uint2* rc = recp + fr;
@@ -3095,7 +3103,7 @@ __global__ void __launch_bounds__(WG) k_lv_emit_walk(const uint8_t* __restrict__
       if (fr == fe) continue;  // no header starts in this window
       R = fe - fr;
       if (R > LW_RPW) {  // more runs than the run list holds (not from the walker's span rule)
-        if (lane == 0) LV_BAIL(rt, lt, p, PF_WALK, 7);
+        if (lane == 0) LV_BAIL(rt, lt, pages, chunks, p, PF_WALK, 7);
         continue;
       }
       le_issue(blob, blob_len, recp + fr, R, x.s.S, x.k, w, nf);

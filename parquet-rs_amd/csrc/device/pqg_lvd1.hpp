@@ -415,7 +415,7 @@ __global__ void __launch_bounds__(WG) k_d1_tab(const uint8_t* __restrict__ blob,
 // One workgroup per page (grid-stride): the segment tables staged through LDS, 64 segments at a
 // time, thread 0 follows them from offset 0.
 __global__ void __launch_bounds__(WG) k_d1_stitch(const uint8_t* __restrict__ blob, const PageWork* __restrict__ pages,
-                                                  int npages, const ChunkWork* chunks, int sel, RunTables rt,
+                                                  int npages, ChunkWork* chunks, int sel, RunTables rt,
                                                   LevelTables lt) {
   __shared__ uint2 tb[64 * D1_ENT];
   __shared__ uint32_t e_s, jn_s, state_s;
@@ -469,7 +469,7 @@ __global__ void __launch_bounds__(WG) k_d1_stitch(const uint8_t* __restrict__ bl
       }
       __syncthreads();
     }
-    if (threadIdx.x == 0 && state_s != 1) LV_BAIL(rt, lt, (uint32_t)p, PF_D1, 8);
+    if (threadIdx.x == 0 && state_s != 1) LV_BAIL(rt, lt, pages, chunks, (uint32_t)p, PF_D1, 8);
   }
 }
 
@@ -492,7 +492,7 @@ __device__ inline uint32_t d1_bits32(const uint32_t* st, uint32_t sb, uint32_t s
 
 template <int OUT>
 __global__ void __launch_bounds__(WG) k_d1_emit(const uint8_t* __restrict__ blob, uint64_t blob_len,
-                                                PageWork* pages, int npages, const ChunkWork* chunks, int sel,
+                                                PageWork* pages, int npages, ChunkWork* chunks, int sel,
                                                 RunTables rt, LevelTables lt) {
   __shared__ D1EmitSmem sm;
   if (lt.ctr[LC_D1] == 0) return;  // no page for the chunk walks (LvCount)
@@ -536,7 +536,7 @@ __global__ void __launch_bounds__(WG) k_d1_emit(const uint8_t* __restrict__ blob
     D1_COUNT(6, rounds + (sm.lastr ? (1ull << 16) : 0ull) + (1ull << 32))
     (void)rounds;
     if (sm.far) {  // the true chain hops past a chunk (runs longer than the writer's): not taken here
-      if (c == 0) LV_BAIL(rt, lt, p, PF_D1, 10);
+      if (c == 0) LV_BAIL(rt, lt, pages, chunks, p, PF_D1, 10);
       continue;
     }
     uint64_t T;
@@ -632,7 +632,7 @@ __global__ void __launch_bounds__(WG) k_d1_emit(const uint8_t* __restrict__ blob
       D1_STAMP(4)
     }
     if (__syncthreads_or(bad)) {
-      if (c == 0) LV_BAIL(rt, lt, p, PF_D1, 9);
+      if (c == 0) LV_BAIL(rt, lt, pages, chunks, p, PF_D1, 9);
       continue;
     }
     if (sel == SS_DEF) {
@@ -645,7 +645,7 @@ __global__ void __launch_bounds__(WG) k_d1_emit(const uint8_t* __restrict__ blob
 }
 
 // The one-bit dense pages of stream sel (def / rep levels): tables, stitch, emit.
-static void lv_launch_d1(const uint8_t* blob, uint64_t blob_len, PageWork* pages, int npages, const ChunkWork* chunks,
+static void lv_launch_d1(const uint8_t* blob, uint64_t blob_len, PageWork* pages, int npages, ChunkWork* chunks,
                          int sel, RunTables rt, LevelTables lt, hipStream_t s) {
 #ifndef PQG_D1_GRID
 #define PQG_D1_GRID 2048

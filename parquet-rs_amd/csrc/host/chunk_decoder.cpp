@@ -1168,6 +1168,8 @@ int pqg_get_timings(pqg_ctx* ctx, pqg_timings* t) {
 }
 
 static_assert(PATH_LEVEL_RUNS == PQG_PATH_LEVEL_RUNS, "device path bit mirrors the header");
+static_assert(PATH_LEVEL_D1 == PQG_PATH_LEVEL_D1 && PATH_LEVEL_HANDBACK == PQG_PATH_LEVEL_HANDBACK,
+              "device path bits mirror the header");
 
 int pqg_ctx_last_paths(pqg_ctx* ctx, uint32_t* mask) {
   if (!ctx || !mask) return PQG_ERR_INVALID;

@@ -94,10 +94,12 @@ struct ChunkResult {
   uint64_t total_bytes;
   uint64_t bad;            // lowest failing page (chunk-relative) and its status: (page << 32) | status;
                            // ~0 when clean
-  uint32_t paths;          // PQG_PATH_* bits only the device knows (PQG_PATH_LEVEL_RUNS: k_lv_plan)
+  uint32_t paths;          // PQG_PATH_* bits only the device knows (PQG_PATH_LEVEL_RUNS, _D1: k_lv_plan;
+                           // PQG_PATH_LEVEL_HANDBACK: lv_bail)
   uint32_t pad;
 };
 constexpr uint32_t PATH_LEVEL_RUNS = 256u;  // mirrors PQG_PATH_LEVEL_RUNS (include/pqgpu.h)
+constexpr uint32_t PATH_LEVEL_D1 = 512u, PATH_LEVEL_HANDBACK = 1024u;  // and PQG_PATH_LEVEL_D1, _HANDBACK
 
 // Outputs per expand tile of the RLE/bit-packed hybrid decoder (device/pqg_runs.hpp).
 constexpr uint32_t RUN_TILE = 4096;

@@ -330,7 +330,7 @@ class RowGroupDecoder:
 # pqg_ctx_last_paths bits (pqgpu.h PQG_PATH_*)
 PATH_PLAIN, PATH_DICT_LEVEL, PATH_DICT_WINDOW, PATH_DICT_TILES = 1, 2, 4, 8
 PATH_BYTES, PATH_DELTA_BYTES, PATH_DELTA, PATH_RLE_BOOL = 16, 32, 64, 128
-PATH_LEVEL_RUNS = 256  # valid once the decode has been synchronised
+PATH_LEVEL_RUNS, PATH_LEVEL_D1, PATH_LEVEL_HANDBACK = 256, 512, 1024  # valid once the decode has been synchronised
 
 
 def make_pages(specs, misalign=0):

@@ -258,8 +258,10 @@ def _mixed_pages(oracle, rng, max_def=1):
 
 
 def test_mixed_paths_in_one_chunk(oracle, ctx):
+    import pqgpu
     rng = np.random.default_rng(6)
     _check(oracle, ctx, _mixed_pages(oracle, rng), True)
+    assert ctx.last_paths() & pqgpu.PATH_LEVEL_D1  # (the third page: the chunk walks)
 
 
 # ------------------------------------------------------------------------------ batches, slots

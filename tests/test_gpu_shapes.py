@@ -345,10 +345,15 @@ def test_level_streams_the_level_path_hands_back(oracle, ctx, nbytes):
 @pytest.mark.gpu
 @pytest.mark.parametrize("long_run", [3000, 70000, 200000])
 def test_dense_level_windows_with_long_runs(oracle, ctx, long_run):
-    """Dense one-bit def-level streams (10% nulls: a header every few bytes, the window path) with
-    one long RLE run in the middle: the window holding it writes tens of thousands of outputs
-    from one run among hundreds of short ones. Runs of ones and of zeros; a dense page without a
-    long run after them."""
+    """Dense one-bit def-level streams (10% nulls: a header every few bytes) with one long RLE run
+    in the middle: the window holding it writes tens of thousands of outputs from one run among
+    hundreds of short ones. Runs of ones and of zeros; a dense page without a long run after them.
+
+    A window-path test: the run lifts the first three pages far above the 7.5 levels per stream
+    byte up to which k_lv_plan gives a dense one-bit page to the chunk walks of pqg_lvd1.hpp
+    (n * 16 <= slen * 120: about 35 000 levels in 5 000 bytes are 6.7 per byte, with the 3 000
+    more of the shortest run 7.6), so only the fourth page takes those. Long runs inside a page of
+    the chunk walks: test_gpu_d1.py::test_long_rle_runs_inside_a_page."""
     rng = np.random.default_rng(long_run)
     pages = []
     for k in range(4):
